@@ -125,6 +125,37 @@ def test_bench_spawns_its_ranks():
     assert r["n_gpus"] == 1 and r["config"]["workload"] == "qwen3-4b"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's output as DIR/<name>.npy in float32, the same in two runs with the same arguments
+    (seeded inputs); --steps sets the number of timed steps and ms_per_step is reported."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    for d in (a, b):
+        r = _bench_line(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "0", "--dry-run", "--dump-outputs", str(d)])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+    ya, yb = np.load(a / "step_output.npy"), np.load(b / "step_output.npy")
+    assert ya.dtype == np.float32 and ya.shape == (1, 256) and np.array_equal(ya, yb)
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """Past the 64 MB budget an output is replaced by a fixed seeded sample of its elements, the same in every run; float64 stays
+    float64, everything else is written as float32; --steps below 1 is refused."""
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    big = np.arange(1 << 16, dtype=np.int32).reshape(256, 256)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"f64": np.ones(3), "big": big}, limit=4096 * 2 + 24 + 1000)
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (250,) and np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert np.all(np.diff(s) > 0) and np.all(np.isin(s, big.astype(np.float32)))
+    assert np.load(tmp_path / "a" / "f64.npy").dtype == np.float64
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bad = subprocess.run([sys.executable, "bench.py", "--steps", "0", "--dry-run"], cwd=root, capture_output=True, text=True, timeout=300)
+    assert bad.returncode != 0 and "--steps" in bad.stderr
+
+
 def test_bench_under_torchrun():
     """The driver's launch line for N > 1: torch.distributed.run, one rank per process, rendezvous on 127.0.0.1."""
     port = _free_port()
