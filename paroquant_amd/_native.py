@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_int, c_int32, c_int64, c_void
 
 import torch  # noqa: F401  -- must be imported first so libamdhip64.so.7 resolves to torch's runtime
 
-PARO_ABI_VERSION = 19
+PARO_ABI_VERSION = 20
 PARO_MAX_PARTS = 8
 PARO_WS_COUNTER_BYTES = 16384
 PARO_WS_STATUS_OFFSET = PARO_WS_COUNTER_BYTES - 4
@@ -64,6 +64,7 @@ EXPORTS = (
     "paro_prompt_row_rms",
     "paro_prompt_qkv_post",
     "paro_prompt_silu_mul",
+    "paro_attn_prompt",
     "paro_allreduce_buffer_bytes",
     "paro_allreduce_buffer_create",
     "paro_allreduce_buffer_open",
@@ -278,6 +279,8 @@ def load() -> ctypes.CDLL:
                                          c_int64, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, c_void_p]
     lib.paro_prompt_silu_mul.restype = c_int
     lib.paro_prompt_silu_mul.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]
+    lib.paro_attn_prompt.restype = c_int
+    lib.paro_attn_prompt.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.paro_parts_finish.restype = c_int
     lib.paro_parts_finish.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]
     lib.paro_allreduce_buffer_bytes.restype = c_int64

@@ -27,7 +27,9 @@ to the reducer route within rounding, not bit for bit).
 
 Embedding lookup, final norm, the (unquantised, fp16) lm_head and the greedy argmax are plain torch ops inside the
 same graph; the token and position live in device tensors, so a replay is one whole token with no host round trip.
-Prefill runs the same weights through ``PackedParoWeights.apply`` (MFMA GEMM) with torch attention.
+Prefill runs the same weights through ``PackedParoWeights.apply`` (MFMA GEMM) with torch attention from position 0; a prompt that
+continues the cached context (``prefill(ids, start_pos > 0)``: a chat turn, a chunk, a rewind) attends over the caches with
+``ops.attn_prompt`` (csrc/attn_prompt.hip).
 """
 from __future__ import annotations
 
@@ -453,29 +455,105 @@ class ParoDecoderLM:
 
     # ------------------------------------------------------------------ prefill (MFMA GEMM path + torch attention)
     @torch.no_grad()
-    def prefill(self, ids: torch.Tensor) -> torch.Tensor:
-        """Run the prompt ``ids`` [T] through the model, fill the KV caches, return the logits of the last position and
-        set (tok, pos) for the first decode step."""
+    def prefill(self, ids: torch.Tensor, start_pos: int = 0, chunk_size: Optional[int] = None) -> torch.Tensor:
+        """Run the prompt ``ids`` [T] through the model at positions ``start_pos .. start_pos + T - 1``, fill the KV caches there,
+        return the logits of the last position and set (tok, pos = start_pos + T) for the first decode step.
+
+        ``start_pos = 0`` starts a new context (the framework's SDPA over the prompt rows).  ``start_pos > 0`` CONTINUES the context
+        the caches hold -- a further chat turn, or a rewind when ``start_pos`` is below ``pos``: the new rows attend to cache positions
+        ``0 .. start_pos + t`` through ``ops.attn_prompt`` (head_dim 64 / 128; ``PARO_PROMPT_TORCH`` does not apply).  ``start_pos``
+        may not exceed ``pos`` (the positions whose K / V the caches hold: one host read).  ``chunk_size = C`` (1 .. 65535) runs the
+        prompt as consecutive chunks of C tokens, the first by the route its position selects, the rest as continuations."""
+        c = self.cfg
+        T = int(ids.numel())
+        start_pos = int(start_pos)
+        if chunk_size is not None and not 1 <= int(chunk_size) <= 65535:
+            raise ValueError(f"chunk_size must be in 1 .. 65535 (got {chunk_size})")
+        if start_pos == 0 and chunk_size is None:
+            return self._prefill_fresh(ids)
+        if T < 1:
+            raise ValueError("empty prompt")
+        if start_pos < 0 or start_pos + T > c.max_positions:
+            raise ValueError(f"positions {start_pos} .. {start_pos + T - 1} are outside max_positions {c.max_positions}")
+        step = T if chunk_size is None else int(chunk_size)
+        if (start_pos > 0 or step < T) and c.head_dim not in (64, 128):
+            raise ValueError(f"continuing a context needs head_dim 64 or 128 (got {c.head_dim})")
+        if start_pos > 0:
+            held = int(self.pos.item())
+            if start_pos > held:
+                raise ValueError(f"start_pos {start_pos} is beyond the {held} positions the caches hold")
+        logits = None
+        for a in range(0, T, step):
+            p, part = start_pos + a, ids[a:a + step]
+            if p == 0:
+                logits = self._prefill_fresh(part)
+            elif self._no_row_group():
+                logits = self._teacher_forced(part.to(self.device), p)
+            else:
+                logits = self._prefill_rows(part, p)
+        return logits
+
+    def _teacher_forced(self, ids_d: torch.Tensor, start_pos: int) -> torch.Tensor:
+        """The prompt through the decode step, one teacher-forced token at a time (``_no_row_group``)."""
+        T = int(ids_d.numel())
+        for i in range(T):
+            self.tok.copy_(ids_d[i:i + 1])
+            self.pos.fill_(start_pos + i)
+            self.decode_step()
+        self.out_tokens[start_pos:start_pos + T] = ids_d
+        return self.logits.clone()                     # tok / pos already hold the first generated token and start_pos + T
+
+    def _reduce_rows(self, part: torch.Tensor) -> torch.Tensor:
+        """RowParallelLinear's all-reduce of [T, hidden] (RCCL / the group's backend); identity on one GPU."""
+        if self.tp_world > 1:
+            dist.all_reduce(part, group=self.tp_group)
+        return part
+
+    def _no_row_group(self) -> bool:
+        """A tensor-parallel rank without a process group to all-reduce [T, hidden] over (the decode step's kernel-level collective is
+        sized for one row): it takes prompts through the decode step, one teacher-forced token at a time."""
+        return self.tp_world > 1 and not (dist.is_available() and dist.is_initialized())
+
+    def _prefill_rows(self, ids: torch.Tensor, start_pos: int) -> torch.Tensor:
+        """The prompt rows at positions ``start_pos ..`` on the fused linears and the three prompt kernels (csrc/prompt.hip, ABI v19 -- row
+        RMS, qkv post-processing into the attention's inputs and the decode caches, SiLU * up: three launches per layer instead of ~45
+        framework operators, which at 128 rows cost more than the linears; Qwen3-4B time to first token 16.8 -> profiles/NOTES.md 6.10).
+        The attention: a new context (``start_pos = 0``) is the framework's SDPA over the new rows; a continuation attends over the caches
+        (``ops.attn_prompt``, csrc/attn_prompt.hip)."""
+        c = self.cfg
+        T = int(ids.numel())
+        ids_d = ids.to(self.device)
+        h = self.embed[ids_d]                                                         # [T, hidden]
+        sdpa = torch.nn.functional.scaled_dot_product_attention
+        for L in self.layers:
+            q, k, v = ops.prompt_qkv_post(L.qkv.apply(h), ops.prompt_row_rms(h, c.rms_eps), self.rope, L.kcache, L.vcache, self.nh, self.nkv,
+                                          c.head_dim, L.q_norm, L.k_norm, c.rms_eps, pos0=start_pos)
+            if start_pos == 0:
+                att = sdpa(q.transpose(0, 1)[None], k.transpose(0, 1)[None], v.transpose(0, 1)[None], is_causal=True,
+                           enable_gqa=self.nh != self.nkv)[0].transpose(0, 1).reshape(T, -1).contiguous()
+            else:
+                att = ops.attn_prompt(q, L.kcache, L.vcache, start_pos)
+            h = h + self._reduce_rows(L.o.apply(att))
+            act = ops.prompt_silu_mul(L.gate_up.apply(h), ops.prompt_row_rms(h, c.rms_eps))
+            h = h + self._reduce_rows(L.down.apply(act))
+        logits = torch.matmul(self._final_norm(h[-1:]), self.lm_head.t())
+        self.out_tokens[start_pos:start_pos + T] = ids_d
+        self.tok.copy_(torch.argmax(logits, dim=-1))
+        self.pos.fill_(start_pos + T)
+        return logits
+
+    def _prefill_fresh(self, ids: torch.Tensor) -> torch.Tensor:
+        """A new context from position 0 (the framework's SDPA over the prompt rows)."""
         c, dt = self.cfg, self.dtype
         T = int(ids.numel())
         if T > c.max_positions:
             raise ValueError("prompt longer than max_positions")
-        sharded = self.tp_world > 1
-        if sharded and not (dist.is_available() and dist.is_initialized()):
-            # no process group to all-reduce [T, hidden] over (the decode step's kernel-level collective is sized for one
-            # row): take the prompt through the decode step, one teacher-forced token at a time
-            ids_d = ids.to(self.device)
-            for i in range(T):
-                self.tok.copy_(ids_d[i:i + 1])
-                self.pos.fill_(i)
-                self.decode_step()
-            self.out_tokens[:T] = ids_d
-            return self.logits.clone()                 # tok / pos already hold the first generated token and T
-
-        def reduce_rows(part):                         # RowParallelLinear's all-reduce of [T, hidden] (RCCL / the group's backend)
-            if sharded:
-                dist.all_reduce(part, group=self.tp_group)
-            return part
+        if self._no_row_group():
+            return self._teacher_forced(ids.to(self.device), 0)
+        # PARO_PROMPT_TORCH=1: the framework expressions of the element-wise work
+        if c.head_dim <= 128 and os.environ.get("PARO_PROMPT_TORCH", "0") != "1":
+            return self._prefill_rows(ids, 0)
+        reduce_rows = self._reduce_rows
         h = self.embed[ids.to(self.device)]                                           # [T, hidden]
         rs = lambda x: torch.rsqrt(x.float().pow(2).mean(-1, keepdim=True) + c.rms_eps)
         half = c.head_dim // 2
@@ -489,24 +567,6 @@ class ParoDecoderLM:
         def headnorm(x, w):
             return x if w is None else ((x.float() * rs(x)).to(dt) * w)
 
-        # The element-wise work between the linears: three launches per layer (csrc/prompt.hip, ABI v19 -- row RMS, qkv post-processing
-        # into the attention's inputs and the decode caches, SiLU * up) instead of ~45 framework operators, which at 128 rows cost more
-        # than the linears (Qwen3-4B time to first token 16.8 -> profiles/NOTES.md 6.10).  PARO_PROMPT_TORCH=1: the framework expressions.
-        if c.head_dim <= 128 and os.environ.get("PARO_PROMPT_TORCH", "0") != "1":
-            sdpa = torch.nn.functional.scaled_dot_product_attention
-            for L in self.layers:
-                q, k, v = ops.prompt_qkv_post(L.qkv.apply(h), ops.prompt_row_rms(h, c.rms_eps), self.rope, L.kcache, L.vcache, self.nh, self.nkv,
-                                              c.head_dim, L.q_norm, L.k_norm, c.rms_eps)
-                att = sdpa(q.transpose(0, 1)[None], k.transpose(0, 1)[None], v.transpose(0, 1)[None], is_causal=True,
-                           enable_gqa=self.nh != self.nkv)[0].transpose(0, 1).reshape(T, -1)
-                h = h + reduce_rows(L.o.apply(att.contiguous()))
-                act = ops.prompt_silu_mul(L.gate_up.apply(h), ops.prompt_row_rms(h, c.rms_eps))
-                h = h + reduce_rows(L.down.apply(act))
-            logits = torch.matmul(self._final_norm(h[-1:]), self.lm_head.t())
-            self.out_tokens[:T] = ids.to(self.device)
-            self.tok.copy_(torch.argmax(logits, dim=-1))
-            self.pos.fill_(T)
-            return logits
         for L in self.layers:
             qkv = (L.qkv.apply(h).float() * rs(h)).to(dt)          # norm weight is folded into the channel scales
             q, k, v = qkv.split([self.nh * c.head_dim, self.nkv * c.head_dim, self.nkv * c.head_dim], dim=-1)   # this rank's heads
@@ -530,17 +590,25 @@ class ParoDecoderLM:
 
     # ------------------------------------------------------------------ generation + the reference's benchmark protocol
     @torch.no_grad()
-    def generate(self, ids: torch.Tensor, max_new_tokens: int, use_graph: bool = True):
-        """Greedy generation.  Returns (tokens [T + new], stats) with the reference's accounting
-        (inference/base.py:62-77): ttft = first token latency, tps = (new - 1) decode tokens / (t_end - t_first)."""
+    def generate(self, ids: torch.Tensor, max_new_tokens: int, use_graph: bool = True, start_pos: int = 0):
+        """Greedy generation.  Returns (tokens [start_pos + T + new]: the whole context, stats) with the reference's accounting
+        (inference/base.py:62-77): ttft = first token latency, tps = (new - 1) decode tokens / (t_end - t_first).
+
+        ``start_pos > 0`` puts the prompt behind the context the caches already hold (``prefill(ids, start_pos)``), e.g. a chat turn:
+        the last returned token has not been consumed yet, so turn 2 is
+            toks, _ = lm.generate(turn1, n)
+            toks, _ = lm.generate(torch.cat([toks[-1:], turn2]), n, start_pos=len(toks) - 1)
+        A graph captured earlier is replayed as it is (it reads the position from the device)."""
         c = self.cfg
         T = int(ids.numel())
-        n_new = min(max_new_tokens, c.max_positions - T)
+        start_pos = int(start_pos)
+        n_new = min(max_new_tokens, c.max_positions - start_pos - T)
         if T < 1 or n_new < 1:
-            raise ValueError(f"nothing to generate: prompt of {T} tokens, max_new_tokens {max_new_tokens}, max_positions {c.max_positions}")
+            raise ValueError(f"nothing to generate: prompt of {T} tokens at position {start_pos}, max_new_tokens {max_new_tokens}, "
+                             f"max_positions {c.max_positions}")
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
-        self.prefill(ids)
+        self.prefill(ids, start_pos=start_pos)
         torch.cuda.synchronize(self.device)
         t_first = time.perf_counter()
         if use_graph and self._graph is None:
@@ -557,7 +625,7 @@ class ParoDecoderLM:
         torch.cuda.synchronize(self.device)
         t_end = time.perf_counter()
         self.out_tokens.index_copy_(0, self.pos.long(), self.tok)
-        toks = self.out_tokens[: T + n_new].clone()
+        toks = self.out_tokens[: start_pos + T + n_new].clone()
         dec = max(n_new - 1, 1)
-        return toks, {"prompt_tokens": T, "new_tokens": n_new, "ttft_s": t_first - t0,
+        return toks, {"prompt_tokens": T, "new_tokens": n_new, "context_tokens": start_pos + T + n_new, "ttft_s": t_first - t0,
                       "decode_tokens_per_s": dec / max(t_end - t_first, 1e-9), "ms_per_token": (t_end - t_first) * 1e3 / dec}

@@ -640,6 +640,37 @@ def prompt_qkv_post(qkv: torch.Tensor, rs: Optional[torch.Tensor], rope: torch.T
     return q, k, v
 
 
+def attn_prompt(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos0: int) -> torch.Tensor:
+    """Causal attention of ``T`` new query rows at positions ``pos0 .. pos0 + T - 1`` over the decode caches (``paro_attn_prompt``): row ``t``
+    attends to cache positions ``0 .. pos0 + t`` (earlier calls' keys and this chunk's, which ``prompt_qkv_post`` has written).
+    ``q [T, n_heads, hd]`` (``prompt_qkv_post``'s q), ``kcache [n_kv_heads, T_max, hd]``, ``vcache [n_kv_heads, hd, T_max]`` -> ``[T, n_heads * hd]``.
+    hd 64 or 128; positions >= ``pos0 + T`` are never read."""
+    dt = q.dtype
+    if q.dim() != 3 or not q.is_contiguous() or dt not in (torch.float16, torch.bfloat16):
+        raise ValueError("q must be a contiguous [T, n_heads, head_dim] fp16 / bf16 tensor")
+    T, n_heads, hd = (int(s) for s in q.shape)
+    if hd not in (64, 128):
+        raise ValueError(f"attn_prompt supports head_dim 64 and 128 (got {hd})")
+    if kcache.dim() != 3 or vcache.dim() != 3:
+        raise ValueError("kcache [n_kv_heads, T_max, head_dim] / vcache [n_kv_heads, head_dim, T_max] must be 3-d")
+    n_kv, T_max = int(kcache.size(0)), int(kcache.size(1))
+    if tuple(kcache.shape) != (n_kv, T_max, hd) or tuple(vcache.shape) != (n_kv, hd, T_max) or kcache.dtype != dt or vcache.dtype != dt \
+            or not kcache.is_contiguous() or not vcache.is_contiguous() or kcache.device != q.device or vcache.device != q.device:
+        raise ValueError("kcache [n_kv_heads, T_max, head_dim] / vcache [n_kv_heads, head_dim, T_max] must be contiguous tensors of q's dtype and device")
+    if n_heads % n_kv or n_heads // n_kv > 64:
+        raise ValueError(f"n_heads {n_heads} must be a multiple of n_kv_heads {n_kv}, at most 64 per KV head")
+    if T_max % 8:
+        raise ValueError("the caches' position count must be a multiple of 8")
+    pos0 = int(pos0)
+    if T < 1 or pos0 < 0 or pos0 + T > T_max:
+        raise ValueError(f"positions {pos0} .. {pos0 + T - 1} are outside the caches' {T_max}")
+    out = torch.empty(T, n_heads * hd, dtype=dt, device=q.device)
+    with torch.cuda.device(q.device):
+        nat.check(nat.load().paro_attn_prompt(q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), T, pos0, n_heads, n_kv, hd, T_max,
+                                              nat.dtype_code(dt), nat.current_stream_ptr(q.device)))
+    return out
+
+
 def prompt_silu_mul(gate_up: torch.Tensor, rs: Optional[torch.Tensor]) -> torch.Tensor:
     """``silu(gate * rs) * (up * rs)`` of the merged gate_up projection's raw output ``[T, 2 I]`` -> ``[T, I]`` (``paro_prompt_silu_mul``)."""
     if gate_up.dim() != 2 or not gate_up.is_contiguous() or gate_up.size(1) % 16 or gate_up.dtype not in (torch.float16, torch.bfloat16):
