@@ -49,6 +49,9 @@ EXPORTS = (
     "paro_lm_head_workspace_bytes",
     "paro_lm_head",
     "paro_argmax_advance",
+    "paro_sample_workspace_bytes",
+    "paro_sample_uniform",
+    "paro_sample_advance",
     "paro_w4a16_gemm",
     "paro_w4a16_linear",
     "paro_w4a16_gemm_grouped",
@@ -137,6 +140,13 @@ class ParoFusion(Structure):
                 ("ar_peers", c_void_p), ("ar_own", c_void_p), ("ar_state", c_void_p), ("ar_world", c_int32), ("ar_rank", c_int32), ("ar_max_elems", c_int64),
                 ("parts_out", c_void_p), ("parts_in", c_void_p), ("x_out", c_void_p), ("parts_out_n", c_int32), ("attn_head_dim", c_int32),
                 ("attn_in", c_void_p), ("attn_tail", POINTER(ParoAttnTail))]
+
+
+class ParoSampleParams(Structure):
+    """``paro_sample_params_t`` (include/paro_abi.h): 24 bytes, kept in device memory."""
+
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("repetition_penalty", ctypes.c_float), ("top_k", c_int32),
+                ("seed", ctypes.c_uint64)]
 
 
 class ParoExperts(Structure):
@@ -246,6 +256,13 @@ def load() -> ctypes.CDLL:
                                  c_int64, c_void_p]
     lib.paro_argmax_advance.restype = c_int
     lib.paro_argmax_advance.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.paro_sample_workspace_bytes.restype = c_int64
+    lib.paro_sample_workspace_bytes.argtypes = [c_int64]
+    lib.paro_sample_uniform.restype = ctypes.c_float
+    lib.paro_sample_uniform.argtypes = [ctypes.c_uint64, c_int64]
+    lib.paro_sample_advance.restype = c_int
+    lib.paro_sample_advance.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                        c_void_p]
     lib.paro_w4a16_gemm.restype = c_int
     lib.paro_w4a16_gemm.argtypes = [POINTER(ParoLinearDesc), c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                     c_void_p]

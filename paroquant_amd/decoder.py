@@ -168,6 +168,8 @@ class ParoDecoderLM:
         self.embed = self.lm_head = self.final_norm = None
         self.rope = rope_table(cfg, self.device)
         self._graph = None
+        self._graph_sampled = None      # the sampled decode step's own graph (generate with temperature > 0 or a repetition penalty)
+        self.sample_prm = self.sample_ws = None
 
     # ------------------------------------------------------------------ construction
     def _alloc_cache(self, layer: _Layer):
@@ -362,9 +364,10 @@ class ParoDecoderLM:
         self.bytes_per_token = sum(pk.nbytes() for L in self.layers for pk in (L.qkv, L.o, L.gate_up, L.down))
 
     # ------------------------------------------------------------------ one decode token (capturable)
-    def decode_step(self) -> None:
+    def decode_step(self, sampled: bool = False) -> None:
         """Consume ``self.tok`` at position ``self.pos``; leave the logits in ``self.logits``, the greedy next token in
-        ``self.tok`` and advance ``self.pos``.  No host synchronisation, no allocation by the fused ops."""
+        ``self.tok`` and advance ``self.pos``.  No host synchronisation, no allocation by the fused ops.  ``sampled``: the same
+        launches up to the logits, then ``ops.sample_advance`` with the parameters in ``self.sample_prm`` chooses the token."""
         c = self.cfg
         R, S = nat.PROLOGUE_RMSNORM, nat.PROLOGUE_SILU_MUL
         torch.index_select(self.embed, 0, self.tok, out=self.h)
@@ -389,7 +392,13 @@ class ParoDecoderLM:
                 ops.w4a16_gemv_fused(h2, L.gate_up, R, c.rms_eps, out=self.gu_buf)
                 ops.w4a16_gemv_fused(self.gu_buf, L.down, S, out=self.part)
                 self.allreduce(self.part, residual=h2, out=h)
-        if self.fused_tail:
+        if sampled:
+            if self.fused_tail:
+                ops.lm_head(h, self.final_norm, self.lm_head, self.logits, c.rms_eps, self.lm_ws)
+            else:
+                torch.matmul(self._final_norm(h), self.lm_head.t(), out=self.logits)
+            ops.sample_advance(self.logits, self.sample_prm, self.tok, self.pos, self.out_tokens, self.sample_ws)
+        elif self.fused_tail:
             ops.lm_head(h, self.final_norm, self.lm_head, self.logits, c.rms_eps, self.lm_ws)
             ops.argmax_advance(self.lm_ws, c.vocab, self.tok, self.pos, self.out_tokens)
         else:
@@ -438,20 +447,32 @@ class ParoDecoderLM:
         x = h.float()
         return (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + self.cfg.rms_eps)).to(self.dtype) * self.final_norm
 
-    def capture(self) -> None:
-        """Capture :meth:`decode_step` in a HIP graph (one warm-up on a side stream first, as torch requires)."""
+    def capture(self, sampled: bool = False) -> None:
+        """Capture :meth:`decode_step` in a HIP graph (one warm-up on a side stream first, as torch requires).  ``sampled``: the
+        sampled step, kept beside the greedy graph as ``_graph_sampled``."""
+        step = (lambda: self.decode_step(True)) if sampled else self.decode_step
         tok0, pos0 = self.tok.clone(), self.pos.clone()
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self.decode_step()
+            step()
         torch.cuda.current_stream(self.device).wait_stream(s)
         self.tok.copy_(tok0); self.pos.copy_(pos0)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):     # a collective library's watchdog thread must not void the capture
-            self.decode_step()
+            step()
         self.tok.copy_(tok0); self.pos.copy_(pos0)
-        self._graph = g
+        if sampled:
+            self._graph_sampled = g
+        else:
+            self._graph = g
+
+    def _sampler(self, temperature, top_k, top_p, repetition_penalty, seed) -> None:
+        """The sampler's device buffers (allocated at the first sampled call) with this call's parameters: a captured sampled step
+        reads them from the device, so later calls only rewrite the 24 bytes."""
+        if self.sample_ws is None:
+            self.sample_ws = ops.sample_workspace(self.device, self.cfg.vocab)
+        self.sample_prm = ops.sample_params(self.device, temperature, top_k, top_p, repetition_penalty, seed, out=self.sample_prm)
 
     # ------------------------------------------------------------------ prefill (MFMA GEMM path + torch attention)
     @torch.no_grad()
@@ -590,8 +611,18 @@ class ParoDecoderLM:
 
     # ------------------------------------------------------------------ generation + the reference's benchmark protocol
     @torch.no_grad()
-    def generate(self, ids: torch.Tensor, max_new_tokens: int, use_graph: bool = True, start_pos: int = 0):
-        """Greedy generation.  Returns (tokens [start_pos + T + new]: the whole context, stats) with the reference's accounting
+    def generate(self, ids: torch.Tensor, max_new_tokens: int, use_graph: bool = True, start_pos: int = 0, temperature: float = 0.0,
+                 top_k: int = -1, top_p: float = 1.0, repetition_penalty: float = 1.0, seed: int = 0):
+        """Greedy generation by default; sampled generation (the reference's GenerationParams, inference/base.py:10-16, handed to HF
+        ``generate`` with do_sample = temperature > 0, transformers/generator.py:50-58) when ``temperature > 0`` or
+        ``repetition_penalty != 1``: every decode step then ends in ``ops.sample_advance`` (csrc/sample.hip; HF's processor order:
+        penalty over the whole context ``out_tokens[0 .. position)``, temperature, top-k, top-p, one draw ``u = ops.sample_uniform(seed,
+        position)`` per generated position) and replays its own graph ``_graph_sampled``, captured once -- later calls only rewrite the
+        parameters in device memory.  The prompt pass is the greedy one; its first token is re-selected from the prompt's logits.  The
+        draw depends on (seed, position) alone, so the same seed repeats a sequence, a rewind redraws the same numbers, and the ranks of
+        a tensor-parallel model -- same logits, same parameters, same seed -- choose the same token with no collective.
+
+        Returns (tokens [start_pos + T + new]: the whole context, stats) with the reference's accounting
         (inference/base.py:62-77): ttft = first token latency, tps = (new - 1) decode tokens / (t_end - t_first).
 
         ``start_pos > 0`` puts the prompt behind the context the caches already hold (``prefill(ids, start_pos)``), e.g. a chat turn:
@@ -606,22 +637,28 @@ class ParoDecoderLM:
         if T < 1 or n_new < 1:
             raise ValueError(f"nothing to generate: prompt of {T} tokens at position {start_pos}, max_new_tokens {max_new_tokens}, "
                              f"max_positions {c.max_positions}")
+        sampled = float(temperature) > 0.0 or float(repetition_penalty) != 1.0
+        if sampled:
+            self._sampler(temperature, top_k, top_p, repetition_penalty, seed)
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
-        self.prefill(ids, start_pos=start_pos)
+        logits = self.prefill(ids, start_pos=start_pos)
+        if sampled:                                # the prompt pass left the greedy token: select again, for position start_pos + T
+            ops.sample_advance(logits.view(-1), self.sample_prm, self.tok, self.pos, self.out_tokens, self.sample_ws, advance=False)
         torch.cuda.synchronize(self.device)
         t_first = time.perf_counter()
-        if use_graph and self._graph is None:
+        if use_graph and (self._graph_sampled if sampled else self._graph) is None:
             tok, pos = self.tok.clone(), self.pos.clone()
-            self.capture()
+            self.capture(sampled)
             self.tok.copy_(tok); self.pos.copy_(pos)
             torch.cuda.synchronize(self.device)
             t_first = time.perf_counter()          # graph capture is a one-time cost, not decode time
+        graph = self._graph_sampled if sampled else self._graph
         for _ in range(n_new - 1):
             if use_graph:
-                self._graph.replay()
+                graph.replay()
             else:
-                self.decode_step()
+                self.decode_step(sampled)
         torch.cuda.synchronize(self.device)
         t_end = time.perf_counter()
         self.out_tokens.index_copy_(0, self.pos.long(), self.tok)

@@ -767,6 +767,70 @@ def argmax_advance(workspace: torch.Tensor, vocab: int, token: torch.Tensor, pos
                                           0 if out_tokens is None else out_tokens.numel(), nat.current_stream_ptr(token.device)))
 
 
+def sample_params(device, temperature: float = 1.0, top_k: int = -1, top_p: float = 1.0, repetition_penalty: float = 1.0, seed: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sampler's ``paro_sample_params_t`` as a 24-byte uint8 device tensor (the reference's GenerationParams, inference/base.py:10-16).
+    The ranges are checked HERE, because the kernel reads the values from device memory: temperature >= 0 (0 = argmax of the penalised
+    scores), 0 < top_p <= 1, repetition_penalty > 0, any integer top_k (<= 0 or >= vocab: off), seed in 0 .. 2^64 - 1.  ``out``: an
+    existing params tensor to rewrite in place (a captured decode step keeps reading it)."""
+    import math
+    temperature, top_p, repetition_penalty = float(temperature), float(top_p), float(repetition_penalty)
+    if not (math.isfinite(temperature) and temperature >= 0.0):
+        raise ValueError(f"temperature must be >= 0 (got {temperature})")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1] (got {top_p})")
+    if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
+        raise ValueError(f"repetition_penalty must be > 0 (got {repetition_penalty})")
+    if isinstance(top_k, bool) or not isinstance(top_k, int):
+        raise ValueError(f"top_k must be an int (got {top_k!r})")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an int in 0 .. 2^64 - 1 (got {seed!r})")
+    top_k = max(-1, min(top_k, 2 ** 31 - 1))       # everything outside 1 .. vocab - 1 means "off"
+    p = nat.ParoSampleParams(temperature, top_p, repetition_penalty, top_k, seed)
+    host = torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8)
+    if out is None:
+        return host.to(device)
+    if out.dtype != torch.uint8 or out.numel() != ctypes.sizeof(nat.ParoSampleParams) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of 24 bytes")
+    out.copy_(host)
+    return out
+
+
+def sample_workspace(device, vocab: int) -> torch.Tensor:
+    """Zeroed scratch of ``sample_advance`` for a vocabulary (``paro_sample_workspace_bytes``); its first four floats are the last
+    call's {kept count, boundary score, Z, u}."""
+    n = nat.load().paro_sample_workspace_bytes(int(vocab))
+    if n < 0:
+        raise ValueError(f"vocab must be in 1 .. 2^31 - 1 (got {vocab})")
+    return torch.zeros(n, dtype=torch.uint8, device=device)
+
+
+def sample_uniform(seed: int, ctr: int) -> float:
+    """The sampler's draw for (seed, ctr) in [0, 1), computed on the host by the function the kernel uses (``paro_sample_uniform``)."""
+    return float(nat.load().paro_sample_uniform(int(seed), int(ctr)))
+
+
+def sample_advance(logits: torch.Tensor, params: torch.Tensor, token: torch.Tensor, pos: torch.Tensor, out_tokens: Optional[torch.Tensor],
+                   workspace: torch.Tensor, advance: bool = True) -> None:
+    """Sampled next token from ``logits`` [vocab] (fp16 / bf16) on the device (``paro_sample_advance``, include/paro_abi.h):
+    ``advance``: ``out_tokens[pos] = token``, select for position pos + 1, ``pos += 1``; otherwise select for position pos and leave
+    pos alone (the first token after a prompt pass).  ``token`` receives the choice; nothing returns to the host."""
+    lib = nat.load()
+    if token.dtype != torch.int64 or pos.dtype != torch.int32 or (out_tokens is not None and out_tokens.dtype != torch.int64):
+        raise RuntimeError("token / out_tokens must be int64 and pos int32")
+    if logits.dtype not in (torch.float16, torch.bfloat16) or not logits.is_contiguous():
+        raise RuntimeError("logits must be a contiguous fp16 / bf16 tensor")
+    if params.dtype != torch.uint8 or params.numel() != ctypes.sizeof(nat.ParoSampleParams):
+        raise RuntimeError("params must be the 24-byte tensor of ops.sample_params")
+    if out_tokens is not None and not out_tokens.is_contiguous():
+        raise RuntimeError("out_tokens must be contiguous")
+    with torch.cuda.device(logits.device):
+        nat.check(lib.paro_sample_advance(logits.data_ptr(), logits.numel(), nat.dtype_code(logits.dtype), params.data_ptr(), token.data_ptr(),
+                                          pos.data_ptr(), None if out_tokens is None else out_tokens.data_ptr(),
+                                          0 if out_tokens is None else out_tokens.numel(), 1 if advance else 0, workspace.data_ptr(),
+                                          workspace.numel(), nat.current_stream_ptr(logits.device)))
+
+
 _workspaces: dict = {}
 
 
